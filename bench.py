@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- training images/sec of the hypernet-conditioned captioning step on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` it is one rank;
    started bare, it launches those N ranks itself before touching the GPU and passes rank 0's line through)
 
@@ -10,15 +10,22 @@ One "step" = hypernet forward -> decoder forward -> cross entropy -> backward ->
 (BASELINE.json configs[1]: GRU decoder + hypernet, 3 style domains, bs=128 per GPU).  Weak scaling:
 the per-GPU batch is fixed.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run sets up, warms up (--warmup steps, then the untimed spin-up windows), times the --steps steps and prints the
+line: `value` (images/s), `ms_per_step`, `config` and `collectives`.  --dump-outputs DIR also writes what the last timed step
+computed (the loss it returned, the model's parameters after its update) as DIR/<name>.npy, float32; such a run skips
+the spin-up and steps in the deterministic-gradient mode, so that the same arguments give the same files; see dump_outputs().
+
+--full adds the side measurements below (HIP events around the dominant kernel inside the timed region, extra steps and
+runs outside it, the CPU baseline):
   roofline     the dominant kernel (adam_rank_kernel on hn_heads.0.2.weight, 115.2 M parameters):
                algorithmic bytes = 24 B/parameter (read W,m,v + write W,m,v) / its measured duration
                (HIP events on the launch stream), against 8 TB/s HBM peak.
                copy_ceiling_gbps: this box's device-to-device copy rate, measured in the same run.
   module_api   SIDE figure (never `value`): the unchanged-driver loop training_step -> backward -> optimizer.step on the
                module API with the optimiser configure_optimizers() returns (caphn.optim.FusedAdam).
-  collectives  what the data-parallel exchange issued: backend, world size, collectives per step, the time the main stream
-               waited for them in front of the optimiser (exposed_us).
+  collectives  (in every line) what the data-parallel exchange issued: backend, world size, collectives per step, the time the
+               main stream waited for them in front of the optimiser (exposed_us); --full adds per-collective times from
+               four extra steps.
   cpu_baseline the CPU oracle (oracle/caphn_oracle.py, a port of the reference's PyTorch path) timed
                on this box's host cores on a bounded sample of the same workload (rank 0, N = 1 only).
 """
@@ -27,6 +34,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for _p in (ROOT, os.path.join(ROOT, "hypernet-image-captioning_amd")):
@@ -40,6 +48,9 @@ METRIC = "training images/sec at 1/2/4/8 MI355X, Flickr30k GRU+hypernet bs=128"
 HBM_PEAK = 8.0e12           # B/s, MI355X_MICROARCH.md chip table
 STEP_ALGO_BYTES = 5.228e9   # whole-step algorithmic HBM bytes at B=128
 DOMINANT_KERNEL_SYMBOL = "adam_rank_kernel<2, true, true, 2, false>"   # instantiation that runs hn_heads.0.2.weight (k = 480) in the step
+DUMP_WHOLE_MAX = 2_000_000  # --dump-outputs: parameters up to this many elements are written whole ...
+DUMP_SAMPLE = 1 << 20       # ... larger ones (the hypernet's two big second-layer weights) as this many seeded positions
+DUMP_LIMIT = 64 << 20       # bytes, all files together
 
 
 class _Vocab:
@@ -143,6 +154,42 @@ def copy_ceiling(dev, nbytes=1_382_400_000, reps=6):
     return 2.0 * nbytes / (min(ts) * 1e-3) / 1e9
 
 
+def roofline_figures(tr, events, alone_ms, ms_step, dev, B):
+    """--full: the line's `roofline` object -- the dominant kernel from the HIP event pairs recorded around it in the timed
+    region, `alone` from the extra steps after it, the copy ceiling measured now."""
+    kts = [a.elapsed_time(b) for a, b in events]
+    kern_ms = float(np.mean(kts)) if kts else float("nan")
+    k0, w0 = tr.shape.heads[0]
+    kbytes = 24.0 * k0 * w0
+    achieved = kbytes / (kern_ms * 1e-3) / 1e9 if kts else None
+    # HBM bytes of one launch of that kernel from the PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE,
+    # gfx950 corrections applied) -- collected separately, summary committed under profiles/
+    traffic = None
+    # (the file names the kernel symbol it was collected on: a figure for another instantiation is not reported)
+    try:
+        pmc = json.load(open(os.path.join(ROOT, "profiles", "r03_pmc_adam_rank.json")))
+        if int(pmc["algorithmic_bytes"]) == int(kbytes) and pmc.get("kernel", "").startswith(DOMINANT_KERNEL_SYMBOL):
+            traffic = pmc["traffic_bytes"]
+    except Exception:  # noqa: BLE001
+        pass
+    ceiling = copy_ceiling(dev) if B == 128 else None
+    roof = {"bound": "hbm", "kernel": "adam_rank_kernel(hn_heads.0.2.weight)",
+            "achieved": achieved, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+            "frac": (achieved / (HBM_PEAK / 1e9)) if achieved else None, "traffic": traffic,
+            "kernel_launches_timed": len(kts), "kernel_ms": kern_ms, "kernel_ms_median": float(np.median(kts)) if kts else None,
+            "kernel_ms_min": float(np.min(kts)) if kts else None, "algorithmic_bytes": kbytes,
+            "copy_ceiling_gbps": ceiling, "frac_of_copy_ceiling": (achieved / ceiling) if (achieved and ceiling) else None,
+            "step_frac": STEP_ALGO_BYTES / (ms_step * 1e-3) / HBM_PEAK if B == 128 else None}
+    if alone_ms:
+        roof["beside"] = ("in the timed region the next forward's feature_fc / init_hidden / W_a f GEMMs run beside this kernel "
+                          "(FusedTrainer.overlap_level 4); `alone` = the same launch with that front forked behind it, 8 extra "
+                          "steps outside the timed region")
+        roof["alone"] = {"kernel_ms": alone_ms, "achieved": kbytes / (alone_ms * 1e-3) / 1e9,
+                         "frac": kbytes / (alone_ms * 1e-3) / HBM_PEAK,
+                         "frac_of_copy_ceiling": (kbytes / (alone_ms * 1e-3) / 1e9 / ceiling) if ceiling else None}
+    return roof
+
+
 def module_api_loop(dev, dims, batches, steps=10, warmup=3):
     """SIDE measurement, never `value`: the loop an UNCHANGED reference driver runs (hypernet_attention.py:136-204 training_step,
     Lightning's backward / gradient_clip_val / optimizer.step, cc_train_hypernet.py:405, :120) on this package's module API --
@@ -181,6 +228,45 @@ def module_api_loop(dev, dims, batches, steps=10, warmup=3):
     del net, opt
     torch.cuda.empty_cache()
     return out
+
+
+def dump_plan(net):
+    """--dump-outputs, fixed before the first step on every rank (a run whose files would exceed DUMP_LIMIT stops before
+    any step or collective): parameter name -> None (written whole) or the positions of its sample.  A parameter above
+    DUMP_WHOLE_MAX elements is sampled at DUMP_SAMPLE positions (sorted, duplicates dropped) drawn from a generator seeded
+    by the name's CRC-32: the same positions in every run."""
+    plan, total = {}, 0
+    for name, p in net.named_parameters():
+        if p.numel() > DUMP_WHOLE_MAX:
+            idx = np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, p.numel(), DUMP_SAMPLE))
+            plan[name] = torch.from_numpy(idx).to(p.device)
+            total += 4 * idx.size
+        else:
+            plan[name] = None
+            total += 4 * p.numel()
+    if total + 4096 > DUMP_LIMIT:                  # (+ the loss tensor: a few floats)
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes of parameters, the limit is {DUMP_LIMIT}")
+    return plan
+
+
+def dump_outputs(out_dir, loss, net, plan):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files in out_dir -- `loss.npy` (the loss
+    tensor the step returned) and `<parameter name>.npy` for every parameter of the model after the step's update, or
+    `<name>.sample.npy` (flat) for one that dump_plan() samples.  Inputs and step count (--warmup + --steps: no spin-up)
+    depend on the arguments alone, and the step runs in the deterministic-gradient mode (caphn_tune key 13), so two runs
+    with the same arguments write identical files.  Returns the bytes written."""
+    arrays = {"loss": loss.detach().float().reshape(-1).cpu().numpy()}
+    for name, p in net.named_parameters():
+        t, idx = p.detach(), plan[name]
+        if idx is None:
+            arrays[name] = t.float().cpu().numpy()
+        else:
+            arrays[name + ".sample"] = t.reshape(-1)[idx].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32, copy=False))
+    return total
 
 
 def bind_to_gpu_numa(local_rank):
@@ -302,7 +388,16 @@ def main():
                     "the style rotates over the three domains step by step, so the fused next-theta GEMV sees a changing input row")
     ap.add_argument("--no-overlap", action="store_true", help="do not issue the next batch's caption-independent "
                     "precompute beside the optimiser")
+    ap.add_argument("--full", action="store_true", help="also take the side measurements: roofline of the dominant kernel "
+                    "(events in the timed region, extra steps and the copy ceiling outside it), per-collective times, "
+                    "module_api, cpu_baseline.  Default: only what `value` and `ms_per_step` need")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (its loss, "
+                    "the updated parameters; the two big hypernet weights as a fixed seeded sample) to DIR/<name>.npy, "
+                    "float32.  Skips the spin-up and steps in the deterministic-gradient mode (caphn_tune 13): the same arguments "
+                    "give the same files")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under a launcher: start the ranks ourselves, before anything touches the GPU in this process
@@ -352,8 +447,16 @@ def main():
         assert _lib.load().caphn_tune(11, {"bf16": 1, "bf16x2": 2}[args.dtype]) == 0
 
     B, T, P, D, F, E, H, V = args.batch, 20, 49, 2048, 200, 200, 200, 9684
+    if args.dump_outputs:
+        # by default the split-K weight gradients and the embedding scatter accumulate with fp32 atomics: their last bits
+        # vary run to run, and Adam carries that into every later step.  The dumped outputs come from the deterministic-
+        # gradient mode (no split-K, destination-major embedding gradient; equal to the default to rounding in a step,
+        # tests/test_gpu_determinism.py), so two runs with the same arguments write the same files.  It costs about 1 ms a
+        # step (profiles/r04_deterministic_mode_ab.txt): a plain run keeps the default, and the line says which one ran
+        assert _lib.load().caphn_tune(13, V) == 0
     torch.manual_seed(1234)                       # identical replicas on every rank
     net = HyperNet(F, E, H, V, _Vocab(), cell=args.cell).to(dev)
+    plan = dump_plan(net) if args.dump_outputs else None
     tr = FusedTrainer(net, lr=1e-3, max_norm=5.0)
     if os.environ.get("CAPHN_OVERLAP_LEVEL"):
         tr.overlap_level = int(os.environ["CAPHN_OVERLAP_LEVEL"])
@@ -451,7 +554,8 @@ def main():
     # every kernel keeps its normal duration, a second process on the same box never shows it --
     # tools/first_steps.py).  Inside a 50-step timed region that one stall reads as 2.8 instead of 2.05 ms/step.
     # Keep stepping in windows of 20 until two consecutive windows agree within 2 % and the last one is within 3 % of
-    # the fastest seen, or 4 s have passed.
+    # the fastest seen, or 4 s have passed.  --dump-outputs skips it: the dumped state is then that of exactly
+    # --warmup + --steps steps from the seeded start, whatever the timing (see dump_outputs()).
     spin = {"steps": 0}
     if args.pretouch > 0:
         tiny = torch.zeros(4, dtype=torch.float32, device=dev)
@@ -464,7 +568,7 @@ def main():
         torch.cuda.synchronize()
         if rank == 0:
             print(f"[pretouch] {args.pretouch} launches in {(time.perf_counter() - t_pt) * 1e3:.1f} ms, slowest single call {worst * 1e3:.2f} ms", file=sys.stderr)
-    if not args.no_spinup:
+    if not (args.no_spinup or args.dump_outputs):
         def window(n=20):
             torch.cuda.synchronize()
             t = time.perf_counter()
@@ -488,7 +592,7 @@ def main():
             if done:
                 break
             prev = cur
-    # dominant-kernel timing: HIP events on the launch stream around the adam_rank launch of head 0
+    # dominant-kernel timing (--full): HIP events on the launch stream around the adam_rank launch of head 0
     from caphn import ops
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     orig = ops.adam_rank
@@ -509,7 +613,8 @@ def main():
                 cnt["i"] += 1
                 return
         orig(W, *a, **k)
-    ops.adam_rank = timed_adam_rank
+    if args.full:
+        ops.adam_rank = timed_adam_rank
 
     barrier()
     t0 = time.perf_counter()
@@ -524,9 +629,12 @@ def main():
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
+    if args.dump_outputs and rank == 0:             # (the replicas' parameters are identical; rank 0's loss is its own batch's)
+        nbytes = dump_outputs(args.dump_outputs, loss, net, plan)
+        print(f"[dump-outputs] {nbytes / 2**20:.1f} MiB written to {args.dump_outputs}", file=sys.stderr)
 
     final_loss = float(loss[0])
-    if dist.is_initialized() and (world > 1 or forced):
+    if args.full and dist.is_initialized() and (world > 1 or forced):
         # per-collective device time: four extra steps OUTSIDE the timed region (every rank takes them) with every collective
         # waited for at once between two events on the communication stream
         tr.time_collectives = True
@@ -541,7 +649,7 @@ def main():
     # region with that front forked behind the pass instead (overlap_level 1) time it undisturbed -- reported as roofline.alone,
     # never as roofline.frac.  (Every rank takes the steps: they are collective.)
     alone_ms = None
-    if tr.overlap_level >= 4 and not (use_graph or args.no_prefetch or args.no_overlap):
+    if args.full and tr.overlap_level >= 4 and not (use_graph or args.no_prefetch or args.no_overlap):
         lvl = tr.overlap_level
         tr.overlap_level = 1
         ev2 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(8)]
@@ -571,22 +679,6 @@ def main():
         phase_report(tr, batches, style)
 
     if rank == 0:
-        kts = [a.elapsed_time(b) for a, b in ev[:cnt["i"]]]
-        kern_ms = float(np.mean(kts)) if kts else float("nan")
-        k0, w0 = tr.shape.heads[0]
-        kbytes = 24.0 * k0 * w0
-        achieved = kbytes / (kern_ms * 1e-3) / 1e9 if cnt["i"] else None
-        # HBM bytes of one launch of that kernel from the PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE,
-        # gfx950 corrections applied) -- collected separately, summary committed under profiles/
-        traffic = None
-        # (the file names the kernel symbol it was collected on: a figure for another instantiation is not reported)
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", "r03_pmc_adam_rank.json")))
-            if int(pmc["algorithmic_bytes"]) == int(kbytes) and pmc.get("kernel", "").startswith(DOMINANT_KERNEL_SYMBOL):
-                traffic = pmc["traffic_bytes"]
-        except Exception:  # noqa: BLE001
-            pass
-        ceiling = copy_ceiling(dev) if B == 128 else None
         ms_step = dt / args.steps * 1e3
         line = {
             "metric": METRIC, "value": B * world * args.steps / dt, "unit": "images/s",
@@ -604,27 +696,15 @@ def main():
                                       (" (one-rank RCCL group, collectives forced)" if forced else ""), "launch": "hipGraph" if use_graph else "eager",
                        "next_theta_in_adam_pass": not (use_graph or args.no_prefetch),
                        "next_precompute_beside_adam": not (use_graph or args.no_prefetch or args.no_overlap),
-                       "spinup_steps": spin["steps"], "host_enqueue_ms_per_step": round(t_host / args.steps * 1e3, 4), "cpu_affinity": numa,
+                       "spinup_steps": spin["steps"], "deterministic_gradients": bool(args.dump_outputs), "host_enqueue_ms_per_step": round(t_host / args.steps * 1e3, 4), "cpu_affinity": numa,
                        "final_loss": final_loss},
-            "roofline": {"bound": "hbm", "kernel": "adam_rank_kernel(hn_heads.0.2.weight)",
-                         "achieved": achieved, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": (achieved / (HBM_PEAK / 1e9)) if achieved else None, "traffic": traffic,
-                         "kernel_launches_timed": len(kts), "kernel_ms": kern_ms, "kernel_ms_median": float(np.median(kts)) if kts else None,
-                         "kernel_ms_min": float(np.min(kts)) if kts else None, "algorithmic_bytes": kbytes,
-                         "copy_ceiling_gbps": ceiling, "frac_of_copy_ceiling": (achieved / ceiling) if (achieved and ceiling) else None,
-                         "step_frac": STEP_ALGO_BYTES / (ms_step * 1e-3) / HBM_PEAK if B == 128 else None},
         }
-        if alone_ms:
-            line["roofline"]["beside"] = ("in the timed region the next forward's feature_fc / init_hidden / W_a f GEMMs run beside this kernel "
-                                          "(FusedTrainer.overlap_level 4); `alone` = the same launch with that front forked behind it, 8 extra "
-                                          "steps outside the timed region")
-            line["roofline"]["alone"] = {"kernel_ms": alone_ms, "achieved": kbytes / (alone_ms * 1e-3) / 1e9,
-                                         "frac": kbytes / (alone_ms * 1e-3) / HBM_PEAK,
-                                         "frac_of_copy_ceiling": (kbytes / (alone_ms * 1e-3) / 1e9 / ceiling) if ceiling else None}
+        if args.full:
+            line["roofline"] = roofline_figures(tr, ev[:cnt["i"]], alone_ms, ms_step, dev, B)
         line["collectives"] = coll
-        if world == 1 and not forced and not args.no_module_api and args.cell == "gru" and args.dtype == "f32":
+        if args.full and world == 1 and not forced and not args.no_module_api and args.cell == "gru" and args.dtype == "f32":
             line["module_api"] = module_api_loop(dev, (B, T, P, D, F, E, H, V), batches)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(B, T, P)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

@@ -3,7 +3,7 @@
 # alternating).  Usage:  bash tools/ab_bench.sh "" "--tune 16=0"   -> runs each argument string twice, alternating, and prints
 # ms/step, the dominant kernel's roofline fraction and its duration for every run.
 set -e
-run() { echo "== $1"; python3 bench.py --steps 30 --warmup 5 $1 2>/dev/null | python3 -c "
+run() { echo "== $1"; python3 bench.py --steps 30 --warmup 5 --full $1 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):

@@ -6,7 +6,7 @@ for rep in 1 2; do
   i=0
   for setting in "$@"; do
     i=$((i+1))
-    env $setting python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-module-api > "$out/s${i}_$rep.json" 2> "$out/s${i}_$rep.err"
+    env $setting python3 bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-module-api > "$out/s${i}_$rep.json" 2> "$out/s${i}_$rep.err"
     echo "[$setting] rep $rep: $(grep -o '"ms_per_step": [0-9.]*' "$out/s${i}_$rep.json") $(grep -o '"kernel_ms": [0-9.]*' "$out/s${i}_$rep.json")"
   done
 done

@@ -3,7 +3,7 @@
 # not split around the score exchange, bit 2 backward transposed mat-vec not split around the d alpha exchange)
 set -e
 for rep in 1 2; do for v in 0 1 6 7 2 4; do
-  echo "== opts $v"; python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-module-api --tune 24=$v 2>/dev/null | python3 -c "
+  echo "== opts $v"; python3 bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-module-api --tune 24=$v 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):

@@ -8,7 +8,7 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d "$out/p_$c" -o pmc -- python3 bench.py --steps 3 --warmup 2 --no-spinup --no-cpu-baseline --no-module-api > "$out/pmc_$c.log" 2>&1
+  rocprofv3 --pmc $c --output-format csv -d "$out/p_$c" -o pmc -- python3 bench.py --steps 3 --warmup 2 --no-spinup --full --no-cpu-baseline --no-module-api > "$out/pmc_$c.log" 2>&1
   cp "$(find "$out/p_$c" -name "*counter_collection.csv" | head -1)" "$out/pmc_$c.csv"
   rm -rf "$out/p_$c"
 done

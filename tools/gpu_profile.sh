@@ -6,8 +6,8 @@ tag=${1:-run}; shift || true
 out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-python3 bench.py --steps 50 --warmup 5 "$@" > "$out/bench.json" 2> "$out/bench.err"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o tr -- python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline "$@" > "$out/prof_bench.log" 2>&1
+python3 bench.py --steps 50 --warmup 5 --full "$@" > "$out/bench.json" 2> "$out/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o tr -- python3 bench.py --steps 30 --warmup 5 --full --no-cpu-baseline "$@" > "$out/prof_bench.log" 2>&1
 f=$(find "$out/prof" -name "*kernel_trace.csv" | head -1)
 cp "$f" "$out/kernel_trace.csv"
 python3 tools/timeline.py "$f" --marker grad_norm_partials --step 20 > "$out/timeline.txt"

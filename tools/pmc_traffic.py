@@ -44,7 +44,7 @@ WANT = [
 
 def main():
     fetch, write = load(sys.argv[1]), load(sys.argv[2])
-    out = {"method": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes of `bench.py --steps 3 --warmup 2 --no-spinup`; "
+    out = {"method": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes of `bench.py --steps 3 --warmup 2 --no-spinup --full`; "
                      "bytes = FETCH_SIZE KB x 1024 x 2 (gfx950 wide-read correction) + WRITE_SIZE KB x 1024; mean over the launches "
                      "of the last two steps", "kernels": []}
     for pat, grid, label, algo in WANT:
