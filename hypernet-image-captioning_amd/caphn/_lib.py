@@ -62,6 +62,14 @@ class RankJob(C.Structure):
                 ("next_pack", c_fp), ("pack_H", C.c_int), ("pack_HA", C.c_int), ("pack_pitch", C.c_int), ("pack_hrows", C.c_int)]
 
 
+class RankLag(C.Structure):
+    _fields_ = [("pending", C.c_int), ("store_mv", C.c_int), ("row_ring", c_fp), ("row_stride", C.c_size_t),
+                ("col_ring", c_fp), ("col_stride", C.c_size_t), ("save_row", c_fp), ("save_col", c_fp)]
+
+
+LAG_MAX = 7
+
+
 class PairPack(C.Structure):
     _fields_ = [("wp", c_fp), ("H", C.c_int), ("HA", C.c_int), ("pitch", C.c_int), ("hrows", C.c_int)]
 
@@ -196,6 +204,12 @@ SIGNATURES = {
     "caphn_adam_rank_gemv_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
                                            c_fp, C.c_size_t, c_fp, C.POINTER(AdamHParams), c_fp, c_fp, c_fp, c_fp]),
     "caphn_adam_rank_multi_f32": (C.c_int, [C.c_int, C.c_int, C.POINTER(RankJob), c_fp, C.POINTER(AdamHParams), c_fp]),
+    "caphn_adam_rank_lag_f32": (C.c_int, [C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.POINTER(AdamHParams),
+                                          C.POINTER(RankLag), c_fp, c_fp, c_fp, c_fp]),
+    "caphn_adam_rank_lag_multi_f32": (C.c_int, [C.c_int, C.c_int, C.POINTER(RankJob), C.POINTER(RankLag), c_fp,
+                                                C.POINTER(AdamHParams), c_fp]),
+    "caphn_adam_rank_settle_f32": (C.c_int, [C.c_int, C.c_int, c_fp, c_fp, C.c_float, C.c_float, C.POINTER(RankLag), c_fp]),
+    "caphn_lazy_moments_period": (C.c_int, []),
     "caphn_hyper_forward_acts": (C.c_int, [C.POINTER(HyperDesc), c_fp, c_fp, c_fp]),
     "caphn_stream_copy_f32": (C.c_int, [C.c_size_t, c_fp, c_fp, c_fp]),
     "caphn_outer_f32": (C.c_int, [C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp]),
@@ -234,7 +248,9 @@ def load():
 
 def check(rc, what):
     if rc != 0:
-        raise CaphnError(f"{what} failed: {_ERR.get(rc, rc)}")
+        e = CaphnError(f"{what} failed: {_ERR.get(rc, rc)}")
+        e.rc = rc
+        raise e
 
 
 def stream_ptr():

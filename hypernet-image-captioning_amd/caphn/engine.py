@@ -136,6 +136,12 @@ class FusedTrainer:
         self.pack_in_adam = os.environ.get("CAPHN_PACK_IN_ADAM", "1") == "1"
         self._fork0_ev = None
         self.ctx_in_forward = os.environ.get("CAPHN_CTX_IN_FORWARD", "1") == "1"
+        # lazy moment write-back of the big rank-1 heads: their m, v go back to memory every K-th step only
+        # (K: caphn_tune key 37), the passes in between replay the pending steps from a ring of saved gradient factors
+        self.lazy_min_elems = 1 << 20      # members with rows * k below this stay eager (the bias heads are launch-bound)
+        self._lag = {}                     # head -> _LagState
+        self._lag_K = 1
+        self._lag_stream = None            # (raw handle, torch stream) the lagged passes were issued on
 
     # ------------------------------------------------------------------ parameter arenas
     def _build_arena(self):
@@ -197,8 +203,9 @@ class FusedTrainer:
         self.W2 = [hyper[f"hn_heads.{i}.2.weight"] for i in range(nh)]
         for w in self.W2:
             w.data = w.data.contiguous()
-        self.W2_m = [torch.zeros_like(w.data) for w in self.W2]
-        self.W2_v = [torch.zeros_like(w.data) for w in self.W2]
+        # (W2_m / W2_v, the properties, settle the lazy moment write-back before they hand these out)
+        self._W2_m = [torch.zeros_like(w.data) for w in self.W2]
+        self._W2_v = [torch.zeros_like(w.data) for w in self.W2]
 
     def _frontend_tensors(self):
         if self.frontend is None:
@@ -785,12 +792,14 @@ class FusedTrainer:
             out = []
             for i in members:
                 gi, ai, o, w, ao, an = segs[i]
-                job = [self.W2[i].data, self.W2_m[i], self.W2_v[i], gi, ai]
+                job = [self.W2[i].data, self._W2_m[i], self._W2_v[i], gi, ai]
                 if prefetch:
                     job += [self._acts_next[ao:ao + an], self._owned[f"hn_heads.{i}.2.bias"].data, self._theta_next[o:o + w]]
                 out.append(job)
             return out
-        if early and self.bias_heads_aside and len(groups) == 3 and groups[1][1] and not groups[0][1] and not groups[2][1]:
+        lagged = self._lag_begin(R, dev_sc is not None)
+        if (early and self.bias_heads_aside and len(groups) == 3 and groups[1][1] and not groups[0][1] and not groups[2][1]
+                and not any(i in lagged for i in groups[1][0])):      # (a lagged head's passes stay on the caller's stream)
             # split front: the two bias heads' launch leaves the caller's stream -- it needs the clip coefficient and the next
             # activations only, so it runs on the caption-side stream beside the W_ih pass (b_ih is then ready long before the gate
             # GEMM behind that pass wants it), and the W_ih and W_hh passes follow each other directly
@@ -805,8 +814,20 @@ class FusedTrainer:
             groups = [groups[0], groups[2]]
             order = [order[0], order[-1]]
         for members, _ in groups:
-            jobs = jobs_of(members)
-            if len(jobs) == 1 and pack is not None and members[0] == 1:
+            lm = [i for i in members if i in lagged]
+            if lm:
+                # lagged members: one launch each whatever the grouping (the results do not depend on it)
+                pk = [pack if (i == 1 and pack is not None and len(members) == 1) else None for i in lm]
+                done = self._lag_issue(lm, jobs_of(lm), pk, prefetch, step, dev_sc, zg)
+                if done and pk[0] is not None:
+                    self._pair_packed = (pack.wp, self._theta_next.data_ptr())
+                members_e = [i for i in members if i not in lm] if done else list(members)
+            else:
+                members_e = members
+            jobs = jobs_of(members_e)
+            if not jobs:
+                pass
+            elif len(jobs) == 1 and pack is not None and members_e[0] == 1:
                 ops.adam_rank_multi(jobs, self._coef, self.lr, step, self.betas, self.eps, dev_scalars=dev_sc, zero_gfac=zg, packs=[pack])
                 self._pair_packed = (pack.wp, self._theta_next.data_ptr())
             elif len(jobs) == 1:
@@ -984,6 +1005,7 @@ class FusedTrainer:
         # refreshed (stream-ordered, from this step's pinned slot) in front of every replay
         self._graph_scalars = True
         try:
+            self._settle_moments()      # a captured graph cannot carry a changing phase: the replayed step is the eager one (K = 1)
             self._begin_step()
             g = self._graphs.get(key)
             if g is None:
@@ -1032,6 +1054,95 @@ class FusedTrainer:
             return self.W2_m[i], self.W2_v[i]
         return self._view(self.flat_m, name), self._view(self.flat_v, name)
 
+    # ------------------------------------------------------------------ lazy moment write-back (big rank-1 heads)
+    @property
+    def W2_m(self):
+        """Adam's first moments of the heads' second-layer weights, current (pending lagged steps are settled on the caller's
+        stream first)."""
+        self._settle_moments()
+        return self._W2_m
+
+    @property
+    def W2_v(self):
+        self._settle_moments()
+        return self._W2_v
+
+    def _lag_join(self):
+        """The caller's stream behind the stream the lagged passes ran on (a no-op while both are the same)."""
+        raw = torch._C._cuda_getCurrentRawStream(self.dev.index if self.dev.index is not None else torch.cuda.current_device())
+        if self._lag_stream is not None and self._lag_stream[0] != raw:
+            cur = torch.cuda.current_stream()
+            cur.wait_stream(self._lag_stream[1])
+            self._lag_stream = (raw, cur)
+        elif self._lag_stream is None:
+            self._lag_stream = (raw, torch.cuda.current_stream())
+
+    def _settle_moments(self):
+        """Bring m, v of every lagged head up to date (replay of the pending steps, one launch per head) on the caller's stream."""
+        if not any(st.pending for st in self._lag.values()):
+            return
+        self._lag_join()
+        for i, st in self._lag.items():
+            if st.pending:
+                ops.adam_rank_settle(self._W2_m[i], self._W2_v[i], st.betas, st.desc(st.pending, True))
+                st.pending = 0
+
+    def _lag_begin(self, R, graph):
+        """Which heads run lagged in this optimiser step.  Settles first whatever would make the pending steps wrong: another
+        period, other betas, a data-parallel group, a captured step, another stream."""
+        K = ops.lazy_moments_period()
+        if R != 1 or dp.active(self.group) or graph or torch.cuda.is_current_stream_capturing():
+            K = 1
+        betas = (float(self.betas[0]), float(self.betas[1]))
+        if K != self._lag_K or any(st.pending and st.betas != betas for st in self._lag.values()):
+            self._settle_moments()
+            if K != self._lag_K:
+                self._lag = {}
+                self._lag_K = K
+        if K == 1:
+            return ()
+        self._lag_join()
+        out = []
+        for i, w in enumerate(self.W2):
+            rows, k = w.shape
+            st = self._lag.get(i)
+            if rows * k < self.lazy_min_elems:
+                if st is not None and st.pending:      # (the threshold was raised under pending steps)
+                    self._settle_moments()
+                continue
+            if st is None:
+                st = self._lag[i] = _LagState(rows, k, K, self.dev)
+            if st.refused:
+                continue
+            if not st.pending:
+                st.betas = betas
+            out.append(i)
+        return out
+
+    def _lag_issue(self, members, jobs, packs, prefetch, step, dev_sc, zg):
+        """The lagged passes of `members` (all lagged).  False: the native side refused a shape before launching anything --
+        those members stay eager from now on and the caller issues this step's eager passes."""
+        sts = [self._lag[i] for i in members]
+        lags = [st.desc(st.pending, st.pending == self._lag_K - 1) for st in sts]
+        try:
+            if len(jobs) == 1 and packs[0] is None:
+                j = jobs[0]
+                kw = dict(next_a=j[5], next_bias=j[6], next_theta=j[7]) if prefetch else {}
+                ops.adam_rank(j[0], j[1], j[2], j[3], j[4], self._coef, self.lr, step, self.betas, self.eps, dev_scalars=dev_sc,
+                              zero_gfac=zg, lag=lags[0], **kw)
+            else:
+                ops.adam_rank_multi(jobs, self._coef, self.lr, step, self.betas, self.eps, dev_scalars=dev_sc, zero_gfac=zg,
+                                    packs=packs, lags=lags)
+        except CaphnError as e:
+            if getattr(e, "rc", 0) not in (-1, -3) or any(st.pending for st in sts):
+                raise
+            for st in sts:
+                st.refused = True
+            return False
+        for st in sts:
+            st.pending = 0 if st.pending == self._lag_K - 1 else st.pending + 1
+        return True
+
     def state_dict(self) -> dict:
         """Optimiser state in torch.optim.Adam's state_dict layout (what Lightning checkpoints for the reference,
         cc_train_hypernet.py:393): state[i] = {step, exp_avg, exp_avg_sq} with i the parameter's position in the reference's
@@ -1053,6 +1164,10 @@ class FusedTrainer:
         names = self.optimizer_param_names()
         if "param_names" in sd and list(sd["param_names"]) != names:
             raise CaphnError("optimiser state was saved for a different parameter list")
+        # the loaded moments are current: pending lagged steps of the previous state are dropped, the phase starts over
+        self._lag_join()
+        for lst in self._lag.values():
+            lst.pending = 0
         st = sd["state"]
         if len(st) not in (0, len(names)):
             raise CaphnError(f"optimiser state holds {len(st)} entries, this trainer has {len(names)} parameters")
@@ -1088,6 +1203,27 @@ class FusedTrainer:
         k, w = self.shape.heads[i]
         ao, an = self._acts_layout[f"a{i}"]
         return ops.outer(self.flat_g[o:o + w].contiguous(), self._acts[ao:ao + an].contiguous())
+
+
+class _LagState:
+    """One lagged head: the ring of K - 1 slots of saved gradient factors (row factors [rows], column factors [k] per slot), the
+    number of steps whose moment update is not in memory yet, and the betas those steps ran with."""
+
+    def __init__(self, rows, k, K, dev):
+        self.rows, self.k, self.K = rows, k, K
+        self.ring_row = torch.zeros(K - 1, _up4(rows), dtype=torch.float32, device=dev)
+        self.ring_col = torch.zeros(K - 1, _up4(k), dtype=torch.float32, device=dev)
+        self.pending = 0
+        self.betas = None
+        self.refused = False
+        self._desc = {}
+
+    def desc(self, pending, store):
+        d = self._desc.get((pending, store))
+        if d is None:
+            save = (None, None) if store else (self.ring_row[pending], self.ring_col[pending])
+            d = self._desc[(pending, store)] = ops.rank_lag(pending, store, self.ring_row, self.ring_col, *save)
+        return d
 
 
 def _tkey(t):

@@ -904,17 +904,68 @@ def adam_dense(p, m, v, g, coef, lr, step, betas=(0.9, 0.999), eps=1e-8, dev_sca
                                      L.stream_ptr()), "caphn_adam_dense_f32")
 
 
+def lazy_moments_period() -> int:
+    """Write-back period K of the moments of the trainer's big rank-1 heads (caphn_tune key 37; 1 = eager).  Host only."""
+    return int(L.load().caphn_lazy_moments_period())
+
+
+def rank_lag(pending, store_mv, row_ring=None, col_ring=None, save_row=None, save_col=None) -> "L.RankLag":
+    """caphn_rank_lag for adam_rank / adam_rank_multi / adam_rank_settle.  row_ring [slots, >= rows] and col_ring [slots, >= k]
+    hold the factors of the `pending` steps whose moment update is not in memory yet (slot 0 the oldest); save_row / save_col
+    (1-D) take this pass's factors and are required unless store_mv."""
+    lg = L.RankLag()
+    lg.pending, lg.store_mv = int(pending), 1 if store_mv else 0
+    if row_ring is not None:
+        assert row_ring.dim() == 2 and col_ring.dim() == 2 and row_ring.stride(1) == 1 and col_ring.stride(1) == 1
+        assert row_ring.shape[0] >= pending and col_ring.shape[0] >= pending
+        lg.row_ring, lg.row_stride = L.ptr(row_ring[0]).value, row_ring.stride(0)
+        lg.col_ring, lg.col_stride = L.ptr(col_ring[0]).value, col_ring.stride(0)
+    if save_row is not None:
+        lg.save_row, lg.save_col = L.ptr(save_row).value, L.ptr(save_col).value
+    lg._hold = (row_ring, col_ring, save_row, save_col)
+    return lg
+
+
+def _lag_fits(lg, rows, k):
+    rr, cr, sr, sc = lg._hold
+    assert rr is None or (rr.shape[1] >= rows and cr.shape[1] >= k), "ring slots are smaller than the member"
+    assert sr is None or (sr.numel() >= rows and sc.numel() >= k), "save slots are smaller than the member"
+
+
+def adam_rank_settle(m, v, betas, lag) -> None:
+    """Replay the pending steps of a lagged member into m, v (they are current afterwards).  betas: those of the pending steps."""
+    lib = L.load()
+    rows, k = m.shape
+    assert v.shape == m.shape
+    _lag_fits(lag, rows, k)
+    L.check(lib.caphn_adam_rank_settle_f32(rows, k, L.ptr(m), L.ptr(v), float(betas[0]), float(betas[1]), C.byref(lag),
+                                           L.stream_ptr()), "caphn_adam_rank_settle_f32")
+
+
 def adam_rank(W, m, v, gfac, afac, coef, lr, step, betas=(0.9, 0.999), eps=1e-8, dev_scalars=None,
-              next_a=None, next_bias=None, next_theta=None, zero_gfac=False) -> None:
+              next_a=None, next_bias=None, next_theta=None, zero_gfac=False, lag=None) -> None:
     """Adam on W [rows,k] with gradient coef * sum_r gfac[r,:,None] * afac[r,None,:] (never materialised).
     With next_a / next_bias / next_theta the pass also emits next_theta = W' next_a + next_bias (the next
-    step's forward GEMV on the updated weights, at no extra HBM traffic).  zero_gfac (one factor only): the pass clears gfac."""
+    step's forward GEMV on the updated weights, at no extra HBM traffic).  zero_gfac (one factor only): the pass clears gfac.
+    lag (rank_lag(...)): the lagged pass of the lazy moment write-back -- m, v in memory are lag.pending steps stale and are
+    stored only when lag.store_mv; W and next_theta are bit-identical to the eager pass.  A shape the lagged row code does not
+    cover raises CaphnError (rc CAPHN_EINVAL / CAPHN_ELIMIT) before anything is launched."""
     lib = L.load()
     hp = _hp(lr, betas, eps, step, dev_scalars, zero_gfac)
     rows, k = W.shape
     R = gfac.shape[0]
     assert gfac.shape[1] == rows and afac.shape[1] == k and afac.shape[0] == R
     assert gfac.stride(1) == 1 and afac.stride(1) == 1
+    if lag is not None:
+        _lag_fits(lag, rows, k)
+        if next_a is not None:
+            assert next_a.numel() == k and next_bias.numel() == rows and next_theta.numel() == rows
+        nxt = [None if t is None else t.data_ptr() for t in (next_a, next_bias, next_theta)]
+        # (W, m, v by raw address: the native side checks their alignment itself and refuses)
+        L.check(lib.caphn_adam_rank_lag_f32(R, rows, k, _raw(W), _raw(m), _raw(v), gfac.data_ptr(), afac.data_ptr(), L.ptr(coef),
+                                            C.byref(hp), C.byref(lag), nxt[0], nxt[1], nxt[2], L.stream_ptr()),
+                "caphn_adam_rank_lag_f32")
+        return
     if next_a is None:
         L.check(lib.caphn_adam_rank_f32(R, rows, k, L.ptr(W), L.ptr(m), L.ptr(v), gfac.data_ptr(), gfac.stride(0),
                                         afac.data_ptr(), afac.stride(0), L.ptr(coef), C.byref(hp), L.stream_ptr()),
@@ -927,10 +978,17 @@ def adam_rank(W, m, v, gfac, afac, coef, lr, step, betas=(0.9, 0.999), eps=1e-8,
                                              L.stream_ptr()), "caphn_adam_rank_gemv_f32")
 
 
-def adam_rank_multi(members, coef, lr, step, betas=(0.9, 0.999), eps=1e-8, dev_scalars=None, zero_gfac=False, packs=None) -> None:
+def _raw(t):
+    L.ptr(t)
+    return C.c_void_p(t.data_ptr())
+
+
+def adam_rank_multi(members, coef, lr, step, betas=(0.9, 0.999), eps=1e-8, dev_scalars=None, zero_gfac=False, packs=None,
+                    lags=None) -> None:
     """adam_rank over several members in one launch (the hypernet's small heads are launch-bound one by one).  members: tuples
     (W, m, v, gfac, afac) or (W, m, v, gfac, afac, next_a, next_bias, next_theta); all with the same number of factors R.
-    packs: per member None or a _lib.PairPack (decoder_pair_pack_desc) -- next_theta is also stored in that packed W_hh copy."""
+    packs: per member None or a _lib.PairPack (decoder_pair_pack_desc) -- next_theta is also stored in that packed W_hh copy.
+    lags: per member a rank_lag(...) (all members, or None): the lagged passes, one launch per member (see adam_rank)."""
     lib = L.load()
     hp = _hp(lr, betas, eps, step, dev_scalars, zero_gfac)
     jobs = (L.RankJob * len(members))()
@@ -950,6 +1008,15 @@ def adam_rank_multi(members, coef, lr, step, betas=(0.9, 0.999), eps=1e-8, dev_s
         for j, pk in zip(jobs, packs):
             if pk is not None:
                 j.next_pack, j.pack_H, j.pack_HA, j.pack_pitch, j.pack_hrows = pk.wp, pk.H, pk.HA, pk.pitch, pk.hrows
+    if lags is not None:
+        assert len(lags) == len(members) and all(lg is not None for lg in lags)
+        arr = (L.RankLag * len(members))()
+        for i, (lg, mb) in enumerate(zip(lags, members)):
+            _lag_fits(lg, *mb[0].shape)
+            C.memmove(C.byref(arr, i * C.sizeof(L.RankLag)), C.byref(lg), C.sizeof(L.RankLag))
+        L.check(lib.caphn_adam_rank_lag_multi_f32(R, len(members), jobs, arr, L.ptr(coef), C.byref(hp), L.stream_ptr()),
+                "caphn_adam_rank_lag_multi_f32")
+        return
     L.check(lib.caphn_adam_rank_multi_f32(R, len(members), jobs, L.ptr(coef), C.byref(hp), L.stream_ptr()), "caphn_adam_rank_multi_f32")
 
 

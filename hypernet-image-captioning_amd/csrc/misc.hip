@@ -429,11 +429,37 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(int nb_s, int R, 
 
 // ------------------------------------------------------------------ Adam (torch.optim.Adam, single-tensor form)
 struct AdamK { float lr_bc1, b1, b2, eps, sqrt_bc2; const float* dev; int zg = 0; };    // zg: rank-1 passes clear their row factor (R == 1)
-__device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v, const AdamK& k) {
+// the two moment lines alone: adam_elem and the replay of pending steps (lazy moment write-back, adam_rank_rows<LAG>) share them
+__device__ __forceinline__ void adam_moments(float g, float& m, float& v, const AdamK& k) {
     m = m + (g - m) * (1.0f - k.b1);                       // exp_avg.lerp_(grad, 1 - beta1)
     v = v * k.b2 + (1.0f - k.b2) * g * g;                  // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
+}
+__device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v, const AdamK& k) {
+    adam_moments(g, m, v, k);
     const float denom = sqrtf(v) / k.sqrt_bc2 + k.eps;     // (sqrt(v) / sqrt(bc2)).add_(eps)
     return p - k.lr_bc1 * (m / denom);                     // addcdiv_(m, denom, -lr / bc1)
+}
+// The lagged rank-1 pass (lazy moment write-back) must round exactly as the eager row pass does: W, theta_next and the settled
+// moments are compared bit for bit.  What the compiler's contraction makes of adam_elem(p, a * r, ...) there decides last bits
+// (read from the eager instantiations' code: d = a r - m is ONE fma on the unrounded product, m + d (1 - b1) an fma, the two
+// products of the v line are rounded and then added, p - lr (m / denom) an fma), and the same source can contract differently in
+// another kernel, even per element.  So the lagged kernels do not leave it to the compiler: the replay of pending steps and the
+// current step both go through this one function with the contraction pinned to the eager pass's.  The eager instantiations keep
+// adam_elem and their code as it was.
+__device__ __forceinline__ void adam_moments_rank1(float a, float r, float& m, float& v, const AdamK& k) {
+#pragma clang fp contract(off)
+    const float g = a * r;
+    const float d = __builtin_fmaf(a, r, -m);
+    m = __builtin_fmaf(1.0f - k.b1, d, m);
+    const float t = (1.0f - k.b2) * g;
+    const float vb = v * k.b2, tg = t * g;
+    v = vb + tg;
+}
+__device__ __forceinline__ float adam_elem_rank1(float p, float a, float r, float& m, float& v, const AdamK& k) {
+#pragma clang fp contract(off)
+    adam_moments_rank1(a, r, m, v, k);
+    const float denom = sqrtf(v) / k.sqrt_bc2 + k.eps;
+    return __builtin_fmaf(-k.lr_bc1, m / denom, p);
 }
 __global__ __launch_bounds__(256) void adam_dense_kernel(size_t n, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                          const float* __restrict__ g, const float* __restrict__ coef, AdamK k, int vec) {
@@ -527,11 +553,24 @@ __device__ __forceinline__ void next_store(const NextGemv& nx, int row, float v)
         nx.pack[((size_t)hh * nx.phrows + (size_t)(q + 1) * nk + kk) * nx.ppitch + c] = v;
     }
 }
-template <int QMAX, int RB, bool NTL, bool NTS, bool MULTI>
+// Lazy moment write-back (R == 1 row path only; caphn_rank_lag): m and v in memory are L steps stale.  The gradient of each of
+// those steps is rank 1, (coef d theta[row]) a[col], and its two factors were saved by the pass of that step: the pass reads the
+// stale moments, replays the L updates in registers (oldest first, the same fp32 operations on the same values as the stored
+// path), applies the current step, and stores m, v only when store_mv says so: 16 + 8 / K bytes per parameter instead of 24.
+struct RankLag {
+    int L, store_mv;
+    const float* row_ring; size_t row_stride;      // slot l (0 = oldest): row_ring + l row_stride, [rows] of gfac[row] * coef
+    const float* col_ring; size_t col_stride;      // col_ring + l col_stride, [k] of afac
+    float* save_row; float* save_col;              // this step's slot (null: nothing to save)
+};
+// LAG: 0 the eager pass, 1 a lagged pass, 2 settle (no current gradient, no access to W: replay the pending steps, store m, v)
+template <int QMAX, int RB, bool NTL, bool NTS, bool MULTI, int LAG = 0>
 __device__ __forceinline__ void adam_rank_rows(int R, int rows, int k, float* W, float* m, float* v,
                                                const float* gfac, size_t ldg, const float* afac, size_t lda,
                                                float c, const AdamK& K, int wave_g, int nwaves, int lane, NextGemv nx,
-                                               const f32x4* a_s /* LDS copy of afac [R][k/4] (R > 1), or null */) {
+                                               const f32x4* a_s /* LDS copy of afac [R][k/4] (R > 1), or null */,
+                                               const RankLag* lg = nullptr, const f32x4* c_s = nullptr /* LDS: col_ring [L][k/4] */) {
+    static_assert(LAG == 0 || !MULTI, "the lagged pass is rank 1");
     const int k4 = k >> 2;
     f32x4 an[QMAX];            // next step's head activations (fused forward GEMV on the updated weights)
 #pragma unroll
@@ -543,7 +582,7 @@ __device__ __forceinline__ void adam_rank_rows(int R, int rows, int k, float* W,
 #pragma unroll
     for (int q = 0; q < QMAX; ++q) {
         const int cidx = lane + 64 * q;
-        a1[q] = (!MULTI && cidx < k4) ? reinterpret_cast<const f32x4*>(afac)[cidx] : f32x4{0.f, 0.f, 0.f, 0.f};
+        a1[q] = (!MULTI && LAG != 2 && cidx < k4) ? reinterpret_cast<const f32x4*>(afac)[cidx] : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     for (int row0 = wave_g * RB; row0 < rows; row0 += nwaves * RB) {
         f32x4 pp[RB][QMAX], mm[RB][QMAX], vv[RB][QMAX];
@@ -557,7 +596,7 @@ __device__ __forceinline__ void adam_rank_rows(int R, int rows, int k, float* W,
                     const f32x4* pw = reinterpret_cast<const f32x4*>(W + base) + cidx;
                     const f32x4* pm = reinterpret_cast<const f32x4*>(m + base) + cidx;
                     const f32x4* pv = reinterpret_cast<const f32x4*>(v + base) + cidx;
-                    pp[i][q] = NTL ? __builtin_nontemporal_load(pw) : *pw;
+                    if constexpr (LAG != 2) pp[i][q] = NTL ? __builtin_nontemporal_load(pw) : *pw;
                     mm[i][q] = NTL ? __builtin_nontemporal_load(pm) : *pm;
                     vv[i][q] = NTL ? __builtin_nontemporal_load(pv) : *pv;
                 }
@@ -572,8 +611,25 @@ __device__ __forceinline__ void adam_rank_rows(int R, int rows, int k, float* W,
         for (int i = 0; i < RB; ++i)
 #pragma unroll
             for (int r = 0; r < (MULTI ? RMAX : 1); ++r)
-                grs[i][r] = (r < R && row0 + i < rows) ? gfac[(size_t)r * ldg + row0 + i] : 0.f;
-        if constexpr (!MULTI) {
+                grs[i][r] = (LAG != 2 && r < R && row0 + i < rows) ? gfac[(size_t)r * ldg + row0 + i] : 0.f;
+        // the pending steps' row factors of these rows, requested with the streams as well: lane l holds step l's (one register
+        // per row; the replay broadcasts it with a lane read)
+        float rrv[RB];
+        if constexpr (LAG != 0) {
+#pragma unroll
+            for (int i = 0; i < RB; ++i)
+                rrv[i] = (lane < lg->L && row0 + i < rows) ? lg->row_ring[(size_t)lane * lg->row_stride + row0 + i] : 0.f;
+        }
+        if constexpr (LAG == 1) {
+            // this step's row factor goes to its ring slot (the product the arithmetic below forms: no coefficient ring); stored by
+            // the lane that clears gfac, the row's last reader.  No launch reads the slot it writes.
+            if (lg->save_row && lane == 0) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i)
+                    if (row0 + i < rows) lg->save_row[row0 + i] = grs[i][0] * c;
+            }
+        }
+        if constexpr (!MULTI && LAG != 2) {
             // caphn_adam_hparams::zero_gfac: this wave is the LAST reader of its rows' factor (d theta in the trainer's gradient
             // arena, which the next backward accumulates into): clear it here instead of with a launch in front of the next forward
             if (K.zg && lane == 0) {
@@ -589,6 +645,22 @@ __device__ __forceinline__ void adam_rank_rows(int R, int rows, int k, float* W,
         for (int i = 0; i < RB; ++i) {
             if (row0 + i >= rows) continue;
             const size_t base = (size_t)(row0 + i) * k;
+            if constexpr (LAG != 0) {
+                // replay: the pending steps' moment updates, oldest first (a run-time loop: one instantiation for every L)
+#pragma unroll 1
+                for (int l = 0; l < lg->L; ++l) {
+                    const float r = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rrv[i]), l));
+#pragma unroll
+                    for (int q = 0; q < QMAX; ++q) {
+                        const int cidx = lane + 64 * q;
+                        if (cidx < k4) {
+                            const f32x4 al = c_s[l * k4 + cidx];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) { float me = mm[i][q][e], ve = vv[i][q][e]; adam_moments_rank1(al[e], r, me, ve, K); mm[i][q][e] = me; vv[i][q][e] = ve; }
+                        }
+                    }
+                }
+            }
             float dot = 0.f;
             float gr[MULTI ? RMAX : 1];
 #pragma unroll
@@ -607,14 +679,34 @@ __device__ __forceinline__ void adam_rank_rows(int R, int rows, int k, float* W,
                                 g += (a_s ? a_s[r * k4 + cidx] : reinterpret_cast<const f32x4*>(afac + (size_t)r * lda)[cidx]) * gr[r];
                     }
                     f32x4 po = pp[i][q], mo = mm[i][q], vo = vv[i][q];
+                    if constexpr (LAG == 2) {
+                        f32x4* qm = reinterpret_cast<f32x4*>(m + base) + cidx;
+                        f32x4* qv = reinterpret_cast<f32x4*>(v + base) + cidx;
+                        if (NTS) { __builtin_nontemporal_store(mo, qm); __builtin_nontemporal_store(vo, qv); }
+                        else { *qm = mo; *qv = vo; }
+                    } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { float me = mo[e], ve = vo[e]; po[e] = adam_elem(po[e], g[e], me, ve, K); mo[e] = me; vo[e] = ve; }
-                    dot += po[0] * an[q][0] + po[1] * an[q][1] + po[2] * an[q][2] + po[3] * an[q][3];
-                    f32x4* qw = reinterpret_cast<f32x4*>(W + base) + cidx;
-                    f32x4* qm = reinterpret_cast<f32x4*>(m + base) + cidx;
-                    f32x4* qv = reinterpret_cast<f32x4*>(v + base) + cidx;
-                    if (NTS) { __builtin_nontemporal_store(po, qw); __builtin_nontemporal_store(mo, qm); __builtin_nontemporal_store(vo, qv); }
-                    else { *qw = po; *qm = mo; *qv = vo; }
+                        for (int e = 0; e < 4; ++e) {
+                            float me = mo[e], ve = vo[e];
+                            if constexpr (LAG != 0) po[e] = adam_elem_rank1(po[e], a1[q][e], gr[0], me, ve, K);
+                            else po[e] = adam_elem(po[e], g[e], me, ve, K);
+                            mo[e] = me; vo[e] = ve;
+                        }
+                        dot += po[0] * an[q][0] + po[1] * an[q][1] + po[2] * an[q][2] + po[3] * an[q][3];
+                        f32x4* qw = reinterpret_cast<f32x4*>(W + base) + cidx;
+                        f32x4* qm = reinterpret_cast<f32x4*>(m + base) + cidx;
+                        f32x4* qv = reinterpret_cast<f32x4*>(v + base) + cidx;
+                        if constexpr (LAG == 1) {
+                            if (NTS) __builtin_nontemporal_store(po, qw); else *qw = po;
+                            if (lg->store_mv) {
+                                if (NTS) { __builtin_nontemporal_store(mo, qm); __builtin_nontemporal_store(vo, qv); }
+                                else { *qm = mo; *qv = vo; }
+                            }
+                        } else {
+                            if (NTS) { __builtin_nontemporal_store(po, qw); __builtin_nontemporal_store(mo, qm); __builtin_nontemporal_store(vo, qv); }
+                            else { *qw = po; *qm = mo; *qv = vo; }
+                        }
+                    }
                 }
             }
             if (nx.a) dots[i] = wave_sum(dot);          // (wave-uniform)
@@ -686,6 +778,28 @@ __global__ __launch_bounds__(256) void adam_rank_kernel(int R, int rows, int k, 
             float me = m[i], ve = v[i]; W[i] = adam_elem(W[i], g * c, me, ve, K); m[i] = me; v[i] = ve;
         }
     }
+}
+// The lagged pass (LAG 1) and the settle launch (LAG 2) of the lazy moment write-back: rank 1, the vector row path only (the host
+// refuses every other shape).  A kernel of its own, so that the eager instantiations above keep their arguments and registers.
+// Dynamic LDS: the pending steps' column factors [L][k/4], indexed at run time (one instantiation for every L).
+template <int RB, int QMAX, int LAG>
+__global__ __launch_bounds__(256) void adam_rank_lag_kernel(int rows, int k, float* W, float* m, float* v, const float* gfac,
+                                                            const float* afac, const float* coef, AdamK K, NextGemv nx, RankLag lg) {
+    extern __shared__ __attribute__((aligned(16))) f32x4 c_lds[];
+    const float c = LAG == 2 ? 0.f : coef[0];
+    if (K.dev) { K.lr_bc1 = K.dev[0]; K.sqrt_bc2 = K.dev[1]; }
+    const int k4 = k >> 2;
+    if (lg.L > 0) {
+        for (int i = threadIdx.x; i < lg.L * k4; i += 256) {
+            const int l = i / k4, cc = i - l * k4;
+            c_lds[i] = reinterpret_cast<const f32x4*>(lg.col_ring + (size_t)l * lg.col_stride)[cc];
+        }
+        __syncthreads();
+    }
+    if (LAG == 1 && lg.save_col && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < k4; i += 256) reinterpret_cast<f32x4*>(lg.save_col)[i] = reinterpret_cast<const f32x4*>(afac)[i];
+    const int wave_g = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4, lane = threadIdx.x & 63;
+    adam_rank_rows<QMAX, RB, true, true, false, LAG>(1, rows, k, W, m, v, gfac, 0, afac, 0, c, K, wave_g, nwaves, lane, nx, nullptr, &lg, c_lds);
 }
 // Several SMALL rank-R members in one launch (blockIdx.y = member): the bias heads of the hypernet are two [600, k] matrices, 11 us
 // of launch-bound kernel each on the optimiser's chain.  Same row code; the members share k's width class and R.
@@ -1245,6 +1359,83 @@ extern "C" int caphn_adam_rank_multi_f32(int R, int njobs, const caphn_rank_job*
 #undef RANK_JOBS
 #undef RANK_JOBS_Q
     return caphn_launch_status();
+}
+
+// ---- lazy moment write-back (caphn_rank_lag): lagged passes and the settle launch ----
+int g_tune_lazy_moments = 4;   // caphn_tune key 37: write-back period K of the trainer's big rank-1 heads (1 = eager)
+extern "C" int caphn_lazy_moments_period(void) { return g_tune_lazy_moments; }
+// What the lagged row code covers: rank 1, k % 4 == 0, k <= 2048, 16-byte aligned streams and factors.  Checked before any launch.
+static int rank_lag_check(int R, int rows, int k, const float* W, const float* m, const float* v, const float* afac, const float* next_a,
+                          const caphn_rank_lag* lag, bool settle) {
+    if (R != 1 || rows <= 0 || k <= 0 || !m || !v || !lag || (!settle && (!W || !afac))) return CAPHN_EINVAL;
+    if (lag->pending < 0 || lag->pending > CAPHN_LAG_MAX) return CAPHN_EINVAL;
+    if (lag->pending > 0 && (!lag->row_ring || !lag->col_ring || lag->row_stride < (size_t)rows || lag->col_stride < (size_t)k)) return CAPHN_EINVAL;
+    if (!settle && !lag->store_mv && (!lag->save_row || !lag->save_col || lag->pending >= CAPHN_LAG_MAX)) return CAPHN_EINVAL;
+    if (k % 4 != 0 || !caphn_aligned16(m) || !caphn_aligned16(v) || (!settle && (!caphn_aligned16(W) || !caphn_aligned16(afac))) ||
+        (next_a && !caphn_aligned16(next_a)) || (lag->pending > 0 && (!caphn_aligned16(lag->col_ring) || lag->col_stride % 4 != 0)) ||
+        (!settle && lag->save_col && !caphn_aligned16(lag->save_col))) return CAPHN_EINVAL;
+    if (k > 2048) return CAPHN_ELIMIT;          // the long-row kernel's shapes stay eager
+    return CAPHN_OK;
+}
+static int rank_lag_launch(int mode, int rows, int k, float* W, float* m, float* v, const float* gfac, const float* afac,
+                           const float* coef, const AdamK& K, NextGemv nx, const caphn_rank_lag* lag, caphn_stream_t stream) {
+    long nb = ((long)rows + 3) / 4;
+    if (nb > g_tune_adam_cap) nb = g_tune_adam_cap;
+    if (nb < 1) nb = 1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RankLag lg{lag->pending, mode == 2 ? 1 : lag->store_mv, lag->row_ring, lag->row_stride, lag->col_ring, lag->col_stride,
+               mode == 2 ? nullptr : lag->save_row, mode == 2 ? nullptr : lag->save_col};
+    const size_t shm = sizeof(float) * (size_t)lag->pending * k;       // <= 7 * 2048 * 4 B
+#define RANK_LAG_Q(RB, Q) do { \
+        if (mode == 2) hipLaunchKernelGGL((adam_rank_lag_kernel<2, Q, 2>), dim3((unsigned)nb), dim3(256), shm, s, rows, k, W, m, v, gfac, afac, coef, K, nx, lg); \
+        else hipLaunchKernelGGL((adam_rank_lag_kernel<RB, Q, 1>), dim3((unsigned)nb), dim3(256), shm, s, rows, k, W, m, v, gfac, afac, coef, K, nx, lg); } while (0)
+    // rows per iteration as the eager pass picks them (four for short rows with the fused GEMV, else two)
+    if (k <= 256) { if (nx.a) RANK_LAG_Q(4, 1); else RANK_LAG_Q(2, 1); }
+    else if (k <= 512) RANK_LAG_Q(2, 2);
+    else if (k <= 1024) RANK_LAG_Q(2, 4);
+    else RANK_LAG_Q(2, 8);
+#undef RANK_LAG_Q
+    return caphn_launch_status();
+}
+extern "C" int caphn_adam_rank_lag_f32(int R, int rows, int k, float* W, float* m, float* v, const float* gfac, const float* afac,
+                                       const float* coef, const caphn_adam_hparams* hp, const caphn_rank_lag* lag,
+                                       const float* next_a, const float* next_bias, float* next_theta, caphn_stream_t stream) {
+    if (!gfac || !coef || !hp || hp->step < 1) return CAPHN_EINVAL;
+    if ((next_a != nullptr) != (next_theta != nullptr) || (next_a != nullptr) != (next_bias != nullptr)) return CAPHN_EINVAL;
+    const int rc = rank_lag_check(R, rows, k, W, m, v, afac, next_a, lag, false);
+    if (rc != CAPHN_OK) return rc;
+    return rank_lag_launch(1, rows, k, W, m, v, gfac, afac, coef, make_adam(hp), NextGemv{next_a, next_bias, next_theta}, lag, stream);
+}
+extern "C" int caphn_adam_rank_lag_multi_f32(int R, int njobs, const caphn_rank_job* jobs, const caphn_rank_lag* lags, const float* coef,
+                                             const caphn_adam_hparams* hp, caphn_stream_t stream) {
+    if (njobs <= 0 || !jobs || !lags || !coef || !hp || hp->step < 1) return CAPHN_EINVAL;
+    for (int i = 0; i < njobs; ++i) {          // every member is checked before the first one is launched
+        const caphn_rank_job& j = jobs[i];
+        if (!j.gfac) return CAPHN_EINVAL;
+        if ((j.next_a != nullptr) != (j.next_theta != nullptr) || (j.next_a != nullptr) != (j.next_bias != nullptr)) return CAPHN_EINVAL;
+        if (j.next_pack && (!j.next_a || j.pack_H <= 0 || j.pack_HA <= 0 || j.pack_HA > j.pack_H || j.pack_pitch < j.pack_H || j.pack_hrows <= 0 ||
+                            (long)j.rows % ((long)j.pack_H * j.pack_H) != 0)) return CAPHN_EINVAL;
+        const int rc = rank_lag_check(R, j.rows, j.k, j.W, j.m, j.v, j.afac, j.next_a, &lags[i], false);
+        if (rc != CAPHN_OK) return rc;
+    }
+    const AdamK K = make_adam(hp);
+    for (int i = 0; i < njobs; ++i) {
+        const caphn_rank_job& j = jobs[i];
+        const int rc = rank_lag_launch(1, j.rows, j.k, j.W, j.m, j.v, j.gfac, j.afac, coef, K,
+                                       NextGemv{j.next_a, j.next_bias, j.next_theta, j.next_pack, j.pack_H, j.pack_HA, j.pack_pitch, j.pack_hrows},
+                                       &lags[i], stream);
+        if (rc != CAPHN_OK) return rc;
+    }
+    return CAPHN_OK;
+}
+extern "C" int caphn_adam_rank_settle_f32(int rows, int k, float* m, float* v, float beta1, float beta2, const caphn_rank_lag* lag,
+                                          caphn_stream_t stream) {
+    const int rc = rank_lag_check(1, rows, k, nullptr, m, v, nullptr, nullptr, lag, true);
+    if (rc != CAPHN_OK) return rc;
+    if (lag->pending == 0) return CAPHN_OK;          // nothing pending: m, v are current
+    AdamK K{};
+    K.b1 = beta1; K.b2 = beta2;
+    return rank_lag_launch(2, rows, k, nullptr, m, v, nullptr, nullptr, nullptr, K, NextGemv{nullptr, nullptr, nullptr}, lag, stream);
 }
 
 extern "C" int caphn_abi_version(void) { return 1; }

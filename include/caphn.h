@@ -574,6 +574,39 @@ typedef struct caphn_rank_job {
 } caphn_rank_job;
 int caphn_adam_rank_multi_f32(int R, int njobs, const caphn_rank_job* jobs, const float* coef, const caphn_adam_hparams* hp,
                               caphn_stream_t stream);
+/* Lazy moment write-back of the rank-1 passes (R == 1, the vector row path: k % 4 == 0, k <= 2048, 16-byte aligned W, m, v, afac).
+ * m and v are consumed by nobody but the next pass over the same element, and their update is a function of the old value and
+ * that step's gradient, which on one rank is (coef d theta[row]) a[col].  A pass that is given the two factors of the previous
+ * `pending` steps reads `pending`-steps-stale m, v, replays those updates in registers (oldest first; the same fp32 operations on
+ * the same values as the stored path, so W and next_theta are bit-identical to the eager pass), applies the current step and
+ * stores m, v only when store_mv != 0: 16 B per parameter instead of 24 on the other launches.  Each lagged pass saves its own
+ * factors (gfac[row] * coef[0] per row, afac per column) to save_row / save_col, the ring slot behind the pending ones; the
+ * caller owns the ring and the counters.  With pending == 0 and store_mv != 0 the pass is the eager one. */
+#define CAPHN_LAG_MAX 7        /* pending steps a pass can replay: the write-back period is at most CAPHN_LAG_MAX + 1 */
+typedef struct caphn_rank_lag {
+    int pending;                               /* steps whose moment update is not in memory yet, 0 .. CAPHN_LAG_MAX */
+    int store_mv;                              /* 1 = this pass writes m, v back (they are current afterwards) */
+    const float* row_ring; size_t row_stride;  /* slot l (0 = oldest) at row_ring + l * row_stride, [rows] floats */
+    const float* col_ring; size_t col_stride;  /* slot l at col_ring + l * col_stride, [k] floats; 16-byte aligned, stride % 4 == 0 */
+    float* save_row; float* save_col;          /* [rows], [k] (16-byte aligned): required when store_mv == 0; no slot that is read */
+} caphn_rank_lag;
+/* caphn_adam_rank_f32 / _gemv_f32 (next_* all NULL or all set) in the lagged form.  Shapes the row path does not cover (R > 1,
+ * k % 4 != 0, misaligned tensors: CAPHN_EINVAL; k > 2048: CAPHN_ELIMIT) are refused BEFORE anything is launched: the caller
+ * stays eager for that member. */
+int caphn_adam_rank_lag_f32(int R, int rows, int k, float* W, float* m, float* v, const float* gfac, const float* afac,
+                            const float* coef, const caphn_adam_hparams* hp, const caphn_rank_lag* lag,
+                            const float* next_a, const float* next_bias, float* next_theta, caphn_stream_t stream);
+/* Several lagged members (lags[i] belongs to jobs[i]; next_pack as in caphn_adam_rank_multi_f32), one launch each; every member
+ * is checked before the first launch. */
+int caphn_adam_rank_lag_multi_f32(int R, int njobs, const caphn_rank_job* jobs, const caphn_rank_lag* lags, const float* coef,
+                                  const caphn_adam_hparams* hp, caphn_stream_t stream);
+/* Settle: replay the pending steps into m, v (no current gradient, no access to W); m, v are current afterwards.  Call before
+ * anything but a lagged pass reads the moments (checkpoints), with the betas of the pending steps. */
+int caphn_adam_rank_settle_f32(int rows, int k, float* m, float* v, float beta1, float beta2, const caphn_rank_lag* lag,
+                               caphn_stream_t stream);
+/* Host only: the write-back period K (1 .. CAPHN_LAG_MAX + 1) set with caphn_tune key 37; 1 = eager.  Performance only: results do
+ * not depend on it. */
+int caphn_lazy_moments_period(void);
 /* dst[0..n) = src[0..n) (n % 4 == 0, 16-byte aligned) with the access pattern of the streaming kernels (non-temporal dwordx4): the
  * copy microbenchmark behind bench.py's roofline.copy_ceiling_gbps. */
 int caphn_stream_copy_f32(size_t n, const float* src, float* dst, caphn_stream_t stream);
@@ -614,6 +647,8 @@ int caphn_outer_f32(int rows, int k, const float* g, const float* a, float* out,
  * backward's two live-row vocabulary GEMMs (dHs, dW_fc), 0 (default) = automatic -- every other value measured equal or slower;
  * key 35: 1 = the backward's side branches end into one another (0 default: measured slower); key 36: 1 = the K = 200 NT products
  * with N >= 1024 (the vocabulary logits) through the K-resident kernel (0 default: 1.09x alone, +12 us in the step).
+ * key 37: write-back period K of the moments of the trainer's big rank-1 heads (1 .. 8; 1 = every step, the eager passes;
+ * caphn_lazy_moments_period reads it).
  * Defaults are the measured-fastest. */
 int caphn_tune(int key, int value);
 
