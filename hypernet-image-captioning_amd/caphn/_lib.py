@@ -173,6 +173,7 @@ SIGNATURES = {
     "caphn_cross_entropy_finish": (C.c_int, [C.c_int, c_fp, c_fp, c_fp, c_fp]),
     "caphn_decoder_profile_ptr": (C.c_void_p, [C.POINTER(DecoderDims), c_fp]),
     "caphn_decoder_rowcount_ptr": (C.c_void_p, [C.POINTER(DecoderDims), c_fp]),
+    "caphn_decoder_region_ptr": (C.c_void_p, [C.POINTER(DecoderDims), c_fp, C.c_int, C.POINTER(C.c_size_t)]),
     "caphn_cross_entropy_fwd_bwd": (C.c_int, [C.c_int, C.c_int, c_fp, c_fp, C.c_int64, c_fp, c_fp, C.c_int, c_fp, c_fp]),
     "caphn_embedding_gather": (C.c_int, [C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp]),
     "caphn_embedding_scatter_add": (C.c_int, [C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp]),

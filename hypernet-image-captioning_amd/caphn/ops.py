@@ -667,6 +667,26 @@ def decoder_rowcount_ptr(dims: DecDims, ws: torch.Tensor) -> int:
     return int(L.load().caphn_decoder_rowcount_ptr(C.byref(cd), C.c_void_p(ws.data_ptr())) or 0)
 
 
+REGION_DGI, REGION_DGH, REGION_DUAH, REGION_DE, REGION_LAST_LIVE, REGION_GATES = range(6)
+
+
+def decoder_region(dims: DecDims, ws: torch.Tensor, which: int) -> torch.Tensor:
+    """View into `ws` of one of the backward's per-step intermediates (caphn_decoder_region_ptr: float32 d gi / d gh [B,T,NG H],
+    d(U_a h) [B,T,H], d e [B,T,P]) or of decoder_prepare_rows' last-live table (int32 [B]).  Tests and tuning."""
+    cd = dims.c()
+    n = C.c_size_t(0)
+    p = L.load().caphn_decoder_region_ptr(C.byref(cd), C.c_void_p(ws.data_ptr()), which, C.byref(n))
+    if not p:
+        raise L.CaphnError(f"no workspace region {which} for {dims}")
+    off = int(p) - ws.data_ptr()
+    v = ws[off:off + 4 * n.value]
+    if which == REGION_LAST_LIVE:
+        return v.view(torch.int32)
+    last = {REGION_DGI: dims.NG * dims.H, REGION_DGH: dims.NG * dims.H, REGION_DUAH: dims.H, REGION_DE: dims.P,
+            REGION_GATES: dims.NG * dims.H}[which]
+    return v.view(torch.float32).view(dims.B, dims.T, last)
+
+
 # ------------------------------------------------------------------ embedding
 def embedding_gather(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     lib = L.load()

@@ -31,6 +31,7 @@ int g_tune_fork = 4;        // 0: one stream; 1: independent branches on side st
                             // the pair kernels run BPTT (512-thread workgroups leave wave slots, registers and 60 KB of LDS per CU
                             // for a GEMM workgroup: 1.987/2.004 -> 1.956/1.958 ms per step), else 1 (a 1024-thread BPTT workgroup
                             // and the GEMM fight for the same CUs: 1-2 % worse, round 1)
+int g_tune_bptt_live = 1;    // caphn_tune key 38: 1 = in live-row mode the pair BPTT kernel starts each caption at its last live step (0: at T - 1)
 int g_tune_join_chain = 0;   // caphn_tune key 35: 1 = the backward's branches 0 and 2 end into branch 1, which alone joins the caller's stream (measured +2..+3 us: off)
 int g_tune_sk_dhs = 0, g_tune_sk_vocab_w = 0;      // experiments (caphn_tune keys 33 / 34): split-K of the two live-row vocabulary GEMMs of the backward, 0 = automatic
 #define RUN(x) do { int _rc = (x); if (_rc != CAPHN_OK) return _rc; } while (0)
@@ -176,6 +177,7 @@ inline Side* side_here() {
 struct Ws {   // float offsets into the workspace
     size_t Y1, f, meanf, h0, c0, Waf, G, Xe, Xg, Hs, Hprev, gates, hn, Cs, Cprev, uah, alphas, idx;
     size_t dHs, dgi, dgh, duah, de, dh0, dc0, ctx, dctx, dXe, dWaf, dmeanf, df, dY1, apart, vtmp, colws, colws_s[3], prof, rowmap;
+    size_t lastlive;            // int [B]: last step of each caption whose target is not ignored, -1 if none (caphn_decoder_prepare_rows)
     size_t xch, xch_floats;     // exchange areas of the pair kernels: forward, then backward (xch_floats each)
     size_t wp;                  // packed recurrent weights of the pair kernels
     // AttentionGru(num_layers > 1): attention cell output / its gradient [B,T,H], layered initial state, dh carry, GEMM temporaries,
@@ -235,6 +237,7 @@ inline Ws layout(const caphn_decoder_dims* d) {
     }
     w.prof = take(64);        // 2 x 8 uint64 phase counters (forward, backward) of the recurrent kernels
     w.rowmap = take(B * T + 4);   // int: [0] = number of valid rows, [4..] = their physical (b*T+t) indices
+    w.lastlive = take(B);
     w.xch_floats = caphn_rec_pair_xch_bytes((int)B, (int)P, (int)H) / sizeof(float);
     w.xch = take(2 * w.xch_floats);
     o = (o + 31) & ~(size_t)31;                                  // 128-byte aligned
@@ -255,11 +258,19 @@ inline Ws layout(const caphn_decoder_dims* d) {
     return w;
 }
 
-// stable compaction of the rows whose target is not ignored: map[0] = count, map[4 + j] = j-th valid row
-__global__ __launch_bounds__(1024) void valid_rows_kernel(int n, const int64_t* __restrict__ tgt, int64_t ignore, int* __restrict__ map) {
+// stable compaction of the rows whose target is not ignored: map[0] = count, map[4 + j] = j-th valid row; and per caption the
+// last step with a live target, last[b] (-1: none; an index, not a count -- live targets need not form a prefix)
+__global__ __launch_bounds__(1024) void valid_rows_kernel(int n, const int64_t* __restrict__ tgt, int64_t ignore, int* __restrict__ map,
+                                                          int B, int T, int* __restrict__ last) {
     __shared__ int wsum[16];
     __shared__ int base_s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int b = tid; b < B; b += 1024) {       // (all T loads of a caption independent of each other: no early exit)
+        int l = -1;
+#pragma unroll 4
+        for (int t = 0; t < T; ++t) if (tgt[(size_t)b * T + t] != ignore) l = t;
+        last[b] = l;
+    }
     if (tid == 0) base_s = 0;
     __syncthreads();
     for (int c0 = 0; c0 < n; c0 += 1024) {
@@ -486,6 +497,25 @@ extern "C" const int* caphn_decoder_rowcount_ptr(const caphn_decoder_dims* d, vo
     return reinterpret_cast<const int*>(static_cast<float*>(ws_) + layout(d).rowmap);
 }
 
+extern "C" float* caphn_decoder_region_ptr(const caphn_decoder_dims* d, void* ws_, int which, size_t* count) {
+    if (!dims_ok(d) || !ws_) return nullptr;
+    const Ws w = layout(d);
+    const size_t BT = (size_t)d->B * d->T, GH = (size_t)w.NG * d->H;
+    const bool lstm = d->cell == CAPHN_CELL_LSTM;
+    size_t off, n;
+    switch (which) {
+        case CAPHN_REGION_DGI: off = w.dgi; n = BT * GH; break;
+        case CAPHN_REGION_DGH: off = lstm ? w.dgi : w.dgh; n = BT * GH; break;      // LSTM: d(gh) == d(gi), one array
+        case CAPHN_REGION_DUAH: off = w.duah; n = BT * d->H; break;
+        case CAPHN_REGION_DE: off = w.de; n = BT * d->P; break;
+        case CAPHN_REGION_LAST_LIVE: off = w.lastlive; n = (size_t)d->B; break;
+        case CAPHN_REGION_GATES: off = w.gates; n = BT * GH; break;
+        default: return nullptr;
+    }
+    if (count) *count = n;
+    return static_cast<float*>(ws_) + off;
+}
+
 extern "C" unsigned long long* caphn_decoder_profile_ptr(const caphn_decoder_dims* d, void* ws_) {
     if (!dims_ok(d) || !ws_) return nullptr;
     return reinterpret_cast<unsigned long long*>(static_cast<float*>(ws_) + layout(d).prof);
@@ -496,7 +526,8 @@ extern "C" int caphn_decoder_prepare_rows(const caphn_decoder_dims* d, const int
     if (!dims_ok(d) || !targets || !ws_) return CAPHN_EINVAL;
     const Ws w = layout(d);
     hipLaunchKernelGGL(valid_rows_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), d->B * d->T, targets,
-                       ignore_index, reinterpret_cast<int*>(static_cast<float*>(ws_) + w.rowmap));
+                       ignore_index, reinterpret_cast<int*>(static_cast<float*>(ws_) + w.rowmap), d->B, d->T,
+                       reinterpret_cast<int*>(static_cast<float*>(ws_) + w.lastlive));
     return caphn_launch_status();
 }
 
@@ -780,6 +811,9 @@ static int decoder_backward_impl(const caphn_decoder_dims* d, const caphn_decode
         a.apart_rows = ang;
         a.WP = ws + w.wp; a.wp_pitch = caphn_rec_pair_pitch(H);
         if (!raw) { a.inith_w = p->inith_w; a.initc_w = lstm ? p->initc_w : nullptr; a.dmean_part = ws + w.dmeanf; a.F = F; }
+        // live-row mode: d logits, hence d Hs, is zero on every row above a caption's last live target, and with no external attention
+        // gradient nothing else enters those steps -- each pair starts at its caption's last live step (caphn_tune key 38)
+        if (g_tune_bptt_live && rmap && !dalphas) a.tstart = reinterpret_cast<const int*>(ws + w.lastlive);
         RUN(caphn_launch_rec_pair_bwd(a, lstm, s));
     } else
     RUN(caphn_launch_rec_bwd(a, lstm, s));

@@ -66,6 +66,9 @@ struct RecBwdArgs {
     int t0 = 0, t1 = 0;                  // time-step window [t0, t1), walked backwards (t1 == 0: T).  A window starts from dh = 0 (dc
                                          // from dc0 when t1 < T) and leaves dh_{t0-1} in dh0 (dc in dc0): the caller adds it to what
                                          // arrives at step t0 - 1
+    const int* tstart = nullptr;         // pair backward kernel, whole-sequence launches only: [B] last step of caption b whose dHs row can
+                                         // be non-zero (-1: none).  The caption's loop starts there with a zero carry and the rows above get
+                                         // +0 in every per-step output; null = every caption starts at t1 - 1
 };
 struct AttnGradArgs {
     int T, P, H, pchunk;

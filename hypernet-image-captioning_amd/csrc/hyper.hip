@@ -935,6 +935,7 @@ extern int g_tune_hops;
 extern int g_tune_vocab_order;
 extern int g_det_vocab;
 extern int g_tune_lazy_moments;
+extern int g_tune_bptt_live;
 int caphn_rec_pair_debug_skip(int v);
 int caphn_rec_pair_debug_opts(int v);
 extern "C" int caphn_tune(int key, int value) {
@@ -972,6 +973,7 @@ extern "C" int caphn_tune(int key, int value) {
     if (key == 23) { if (value < 0 || value > 7) return CAPHN_EINVAL; g_tune_gemm_db = value; return CAPHN_OK; }
     if (key == 22) { if (value < 1) return CAPHN_EINVAL; g_tune_xch_timeout = 100ll * value; return CAPHN_OK; }
     if (key == 37) { if (value < 1 || value > CAPHN_LAG_MAX + 1) return CAPHN_EINVAL; g_tune_lazy_moments = value; return CAPHN_OK; }
+    if (key == 38) { g_tune_bptt_live = value != 0; return CAPHN_OK; }
     if (key == 14) { if (value < 64 || value > 65535) return CAPHN_EINVAL; g_tune_adam_cap = value; return CAPHN_OK; }
     return CAPHN_EINVAL;
 }

@@ -769,9 +769,44 @@ __global__ __launch_bounds__(NT) void rec_pair_bwd_kernel(RecBwdArgs a) {
             else { pf[5] = a.hn[bt * H + k]; pf[6] = a.Hprev[bt * H + k]; }
         }
     };
-    if (pfk) prefetch(bt1 - 1);
+    // a.tstart: a step above the caption's last live one receives d Hs == 0 on top of a zero carry and writes nothing but zeros, so the
+    // loop starts at the last live step and the rows above it get their zeros here (the GEMMs behind this kernel read all B T rows).
+    // Both halves of a pair read the same entry: they skip the same steps and exchange the same tag sequence.  A workgroup that
+    // ends early leaves its CU to whatever else is queued (the vocabulary weight gradient on the backward's branch 0)
+    const int tl = a.tstart ? max(min(bt1 - 1, a.tstart[b]), bt0 - 1) : bt1 - 1;
+    if (tl < bt1 - 1) {
+        const size_t r0 = (size_t)b * T + tl + 1;
+        const int nrow = bt1 - 1 - tl;
+        if (vecS) {
+            const int n4 = nk >> 2;
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            for (int i = tid; i < nrow * NG * n4; i += NT) {
+                const int c = i % n4, rq = i / n4, q = rq % NG, r = rq / NG;
+                const size_t o = (r0 + r) * GH + (size_t)q * H + k0;
+                reinterpret_cast<f32x4*>(a.dgi + o)[c] = z;
+                if (!LSTM) reinterpret_cast<f32x4*>(a.dgh + o)[c] = z;
+            }
+            for (int i = tid; i < nrow * n4; i += NT) {
+                const int c = i % n4, r = i / n4;
+                reinterpret_cast<f32x4*>(a.duah + (r0 + r) * H + k0)[c] = z;
+            }
+        } else {
+            for (int i = tid; i < nrow * NG * nk; i += NT) {
+                const int kk = i % nk, rq = i / nk, q = rq % NG, r = rq / NG;
+                const size_t o = (r0 + r) * GH + (size_t)q * H + k0 + kk;
+                a.dgi[o] = 0.f;
+                if (!LSTM) a.dgh[o] = 0.f;
+            }
+            for (int i = tid; i < nrow * nk; i += NT) {
+                const int kk = i % nk, r = i / nk;
+                a.duah[(r0 + r) * H + k0 + kk] = 0.f;
+            }
+        }
+        if (hh == 0) for (int i = tid; i < nrow * P; i += NT) a.de[r0 * P + i] = 0.f;
+    }
+    if (pfk && tl >= bt0) prefetch(tl);
 
-    for (int t = bt1 - 1; t >= bt0; --t) {
+    for (int t = tl; t >= bt0; --t) {
         const size_t bt = (size_t)b * T + t;
         if (pfk) { if (tid < P) al_s[tid] = pfa; }
         else for (int p = tid; p < P; p += NT) al_s[p] = a.alphas[bt * P + p];

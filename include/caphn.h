@@ -303,7 +303,13 @@ typedef struct caphn_pair_pack { float* wp; int H, HA, pitch, hrows; } caphn_pai
 int caphn_decoder_pair_prep(const caphn_decoder_dims* d, const caphn_decoder_params* p, void* ws, caphn_stream_t stream);
 int caphn_decoder_pair_pack_desc(const caphn_decoder_dims* d, void* ws, caphn_pair_pack* out);
 /* Compacts the (b,t) rows whose target differs from ignore_index into a row map kept in the workspace (count stays on
- * the device: no host synchronisation).  Call before caphn_decoder_forward / _backward with dims.row_subset = 1. */
+ * the device: no host synchronisation).  Call before caphn_decoder_forward / _backward with dims.row_subset = 1.
+ * The same launch leaves, in an int[B] field of the workspace, each caption's LAST live step (the largest t whose target is
+ * not ignored; -1 for a caption without one; live targets need not form a prefix).  With dims.row_subset = 1, no dalphas and
+ * caphn_tune key 38 at its default 1, the backward's two-workgroups-per-caption BPTT kernel starts caption b at that step
+ * instead of at T - 1: above it d logits is zero by the row_subset contract, so d Hs and the carried gradient are zero and
+ * every per-step output is zero -- the kernel writes +0 into those rows itself and its workgroups leave their CUs early.
+ * Gradients are bit for bit those of key 38 = 0 (only the sign of exact zeros in workspace intermediates may differ). */
 /* Device address of the live-row count that caphn_decoder_prepare_rows leaves in the workspace. */
 const int* caphn_decoder_rowcount_ptr(const caphn_decoder_dims* d, void* ws);
 int caphn_decoder_prepare_rows(const caphn_decoder_dims* d, const int64_t* targets, int64_t ignore_index,
@@ -311,6 +317,12 @@ int caphn_decoder_prepare_rows(const caphn_decoder_dims* d, const int64_t* targe
 /* Tuning aid: device address of 16 64-bit counters in the workspace -- per-phase shader-clock sums of workgroup 0 of the
  * recurrent forward ([0..8)) and backward ([8..16)) kernels, written only by a library built with -DCAPHN_REC_PROFILE. */
 unsigned long long* caphn_decoder_profile_ptr(const caphn_decoder_dims* d, void* ws);
+/* Test and tuning aid: device address and element count of one of the backward's per-step intermediates inside the workspace
+ * ([B,T,NG H] d gi and d gh -- one array for the LSTM --, [B,T,H] d(U_a h), [B,T,P] d e, all float) or of the int[B] last-live
+ * table of caphn_decoder_prepare_rows (same address type; read it as int).  NULL for bad arguments. */
+enum { CAPHN_REGION_DGI = 0, CAPHN_REGION_DGH = 1, CAPHN_REGION_DUAH = 2, CAPHN_REGION_DE = 3, CAPHN_REGION_LAST_LIVE = 4,
+       CAPHN_REGION_GATES = 5 /* [B,T,NG H] the forward's saved gate activations */ };
+float* caphn_decoder_region_ptr(const caphn_decoder_dims* d, void* ws, int which, size_t* count);
 /* Free-running / scheduled-sampling forward (validation, inference; keeps no backward state).
  * use_sampling is a HOST array of T flags: the reference's per-step draw np.random.random() < sample_prob
  * (decoderlstm.py:79-80); entry 0 is ignored (step 0 never samples).  A sampling step feeds back
@@ -649,6 +661,8 @@ int caphn_outer_f32(int rows, int k, const float* g, const float* a, float* out,
  * with N >= 1024 (the vocabulary logits) through the K-resident kernel (0 default: 1.09x alone, +12 us in the step).
  * key 37: write-back period K of the moments of the trainer's big rank-1 heads (1 .. 8; 1 = every step, the eager passes;
  * caphn_lazy_moments_period reads it).
+ * key 38: 1 (default) = with dims.row_subset and no dalphas the pair BPTT kernel starts each caption at its last live step
+ * (caphn_decoder_prepare_rows); 0 = every caption walks all T steps (same gradients bit for bit).
  * Defaults are the measured-fastest. */
 int caphn_tune(int key, int value);
 
